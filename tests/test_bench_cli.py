@@ -27,6 +27,38 @@ def test_gpus_zero_is_rejected():
     assert r.returncode != 0 and "must be >= 1" in r.stderr
 
 
+def test_steps_must_be_positive():
+    r = _run(["--gpus", "1", "--steps", "0"])
+    assert r.returncode != 0 and "--steps 0 must be >= 1" in r.stderr
+
+
+def test_help_lists_full_and_dump_outputs():
+    r = _run(["--help"])
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+
+
+def test_words16_is_exact():
+    import numpy as np
+    vals = [0, 1, 0xFFFF, 0x0123456789ABCDEF, (1 << 64) - 1]
+    w = bench._words16(vals)
+    assert w.dtype == np.float64 and w.shape == (5, 4)
+    assert [sum(int(w[i, k]) << (16 * k) for k in range(4)) for i in range(5)] == vals
+
+
+def test_prepared_logs_are_keyed_by_the_generator_and_skipped_without_a_gpu():
+    d = bench.prepared_log_dir()
+    assert os.path.dirname(d) == os.path.join(ROOT, "build", "bench_logs") and len(os.path.basename(d)) == 16
+    assert d == bench.prepared_log_dir()
+    if not os.path.exists("/dev/kfd"):
+        assert bench.prepare_inputs() is None
+    # the prepared configuration is the one a plain `bench.py --gpus 1` run generates
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import argparse
+    a = argparse.Namespace(seed=bench.DEFAULT_SEED, new_length_calc=False, **bench.WORKLOADS[bench.HEADLINE])
+    cfg = bench.log_cfg(a)
+    assert (cfg.seed, cfg.n_ops, cfg.n_clients, cfg.lag) == (bench.DEFAULT_SEED * 1000003, 10000, 8, 128)
+
+
 def test_gen_plan_splits_cpus_over_ranks():
     # a 16-CPU quota shared by 8 ranks: 2 generator threads each, not 16
     assert bench.gen_plan(12500, 10000, 16, 8, 0)[0] == 2

@@ -27,7 +27,7 @@ def test_bench_two_ranks_share_one_gpu():
     env.pop("MTB_NO_TORCH", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps",
-           "2", "--warmup", "1", "--docs-total", "300", "--ops", "600", "--traffic", "off"]
+           "2", "--warmup", "1", "--docs-total", "300", "--ops", "600", "--full", "--traffic", "off"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -46,7 +46,7 @@ def test_bench_gpus_2_without_launcher():
     for k in ("MTB_NO_TORCH", "WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--docs-total", "300", "--ops", "600", "--traffic", "off"]
+           "--docs-total", "300", "--ops", "600", "--full", "--traffic", "off"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

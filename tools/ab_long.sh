@@ -12,7 +12,7 @@ for r in 1 2; do
   i=0
   for lib in fluidframework_amd/libmtb.so "$@"; do
     v=v$i$r; i=$((i+1))
-    MTB_LIB=$lib timeout -k 10 600 python3 -u bench.py --workload long-doc --no-cpu --no-summary --traffic off --parity-sample 1 > $O/$v.json 2> $O/$v.err
+    MTB_LIB=$lib timeout -k 10 600 python3 -u bench.py --full --workload long-doc --no-cpu --no-summary --traffic off --parity-sample 1 > $O/$v.json 2> $O/$v.err
     rc=$?; [ $rc -ne 0 ] && { echo "$v rc=$rc"; tail -3 $O/$v.err; exit $rc; }
     python3 -c "import json; d=json.load(open('$O/$v.json')); print('$v', '$lib', round(d['value']), 'ops/s', d['roofline']['kernel_ms'], 'ms', 'mismatches', d['parity']['mismatches'])"
   done

@@ -13,7 +13,7 @@ for r in 1 2; do
   for val in "$@"; do
     v=v$i$r; i=$((i+1))
     if [ "$val" = - ]; then unset $VAR; else export $VAR="$val"; fi
-    timeout -k 10 600 python3 -u bench.py --no-cpu --no-summary --traffic off > $O/$v.json 2> $O/$v.err
+    timeout -k 10 600 python3 -u bench.py --full --no-cpu --no-summary --traffic off > $O/$v.json 2> $O/$v.err
     rc=$?; [ $rc -ne 0 ] && { echo "$v rc=$rc"; tail -3 $O/$v.err; exit $rc; }
     python3 -c "import json; d=json.load(open('$O/$v.json')); print('$v', '$VAR=$val', round(d['value']/1e6,2), 'M ops/s', d['roofline']['kernel_ms'], 'ms', 'mismatches', d['parity']['mismatches'])"
   done
